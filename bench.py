@@ -19,12 +19,16 @@ reduction of the timed interval. `--gpus N` works both ways:
 Default weak scaling: 4096 blocks per GPU (config 2 per GPU). `--total-blocks 1048576` is
 config 5's strong-scaling split (131,072 blocks = 8 GiB per GPU at N = 8).
 
-The `roofline` object is for the dominant kernel of the step; `roofline_decode` is the
-north_star's decode figure (C + U per launch of the decoder over its launch time). Kernel
-times come from HIP events recorded inside the library on the launch stream over the timed
-steps. `cpu_baseline` times the CPU port of the reference path (oracle/: the lz4_flex
-FrameEncoder/FrameDecoder restatement) on every host core over a bounded sample of the same
-workload (rank 0, N = 1 only): median of 5 runs of >= 1 s.
+A plain run sets up, warms up, times the steps and prints the line: `value`, `ms_per_step` and
+the two rooflines that the timed steps' own HIP events give (the match finder k_enc_parse, and
+`roofline_decode`, the north_star's decode figure: C + U per launch of the whole decode over
+its launch time). `--dump-outputs DIR` also writes what the last timed step computed as .npy
+files. Everything else is behind `--full`: the output checks (the gate after the warm-up and
+every decoded byte after the timed steps), `--profile-steps` extra steps with every phase timed
+(`kernel_ms_per_step`, which kernel dominates, `roofline_decode_kernels`) and `cpu_baseline`,
+which times the CPU port of the reference path (oracle/: the lz4_flex FrameEncoder/FrameDecoder
+restatement) on every host core over a bounded sample of the same workload (rank 0, N = 1
+only): median of 5 runs of >= 1 s.
 """
 import argparse
 import json
@@ -51,14 +55,19 @@ def parse_args(argv=None):
     ap.add_argument("--blocks", type=int, default=4096, help="64 KiB blocks per GPU (config 2: 4096; weak scaling)")
     ap.add_argument("--total-blocks", type=int, default=0,
                     help="strong scaling instead: split this many blocks over the ranks (config 5: 1048576)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also check the outputs, time every phase in extra steps (kernel_ms_per_step, the dominant "
+                         "kernel's roofline) and run the CPU baseline; a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--pipeline", action="store_true",
                     help="two queues: step k's decode overlaps step k+1's encode (rooflines then include overlap)")
     ap.add_argument("--profile-steps", type=int, default=3,
-                    help="extra steps after the timed region, every phase timed (kernel_ms_per_step)")
+                    help="with --full: extra steps after the timed region, every phase timed (kernel_ms_per_step)")
     ap.add_argument("--no-kernel-timing", action="store_true",
                     help="diagnostics: no HIP events in the timed steps (no roofline; measures the events' cost)")
-    ap.add_argument("--skip-check", action="store_true", help="diagnostic builds only: skip output checks")
+    ap.add_argument("--skip-check", action="store_true", help="with --full, diagnostic builds only: skip output checks")
     ap.add_argument("--cpu-seconds", type=float, default=1.0, help="wall seconds of each of the 5 CPU baseline runs")
     ap.add_argument("--selftest", action="store_true",
                     help="launcher/rank plumbing only (no GPU): every rank reports in, rank 0 prints the summary")
@@ -330,7 +339,7 @@ def roofline_whole_decode(kt, alg_bytes, profiled_shape: bool, whole=None):
     """(C + U) per step over the average time of the whole decode: `whole` = (ms, launches) of the
     timed steps' single span over the three phases (frame walk, block decode, verify); without it
     the summed averages of the phases' own event pairs."""
-    parts = [p for p in DECODE_PHASES if p in kt]
+    parts = [p for p in DECODE_PHASES if p in kt] or (list(DECODE_PHASES) if whole else [])
     ms = whole[0] / whole[1] if whole else sum(kt[p][0] / kt[p][1] for p in parts)
     achieved = alg_bytes / (ms / 1e3) / 1e9
     traffic, tsrc = None, None
@@ -359,6 +368,59 @@ def roofline_whole_decode(kt, alg_bytes, profiled_shape: bool, whole=None):
 def chunk_seed(rank: int, c: int) -> int:
     import synth
     return synth.SEED_BASE + 1 + 1000 * rank + 7919 * c
+
+
+# ------------------------------------------------------------------ --dump-outputs
+DUMP_SAMPLE = 1 << 20  # elements kept of each byte array (4 MiB as float32)
+DUMP_SEED = 0x5EED0D0D
+
+
+def _sample_bytes(buf, nbytes: int, tag: int):
+    """float32 values of DUMP_SAMPLE bytes of buf[:nbytes] at seeded positions (the whole of a
+    shorter array). The positions are fixed fractions of the length, so the shape is the same
+    whatever nbytes is and two builds that write the same bytes dump the same array."""
+    import numpy as np
+
+    if nbytes <= DUMP_SAMPLE:
+        return np.frombuffer(buf.read(nbytes), dtype=np.uint8).astype(np.float32)
+    u = np.sort(np.random.default_rng(DUMP_SEED + tag).random(DUMP_SAMPLE))
+    idx = np.minimum((u * nbytes).astype(np.int64), nbytes - 1)
+    out = np.empty(DUMP_SAMPLE, dtype=np.float32)
+    piece = 64 << 20  # read back 64 MiB at a time
+    for lo in range(0, nbytes, piece):
+        a, b = np.searchsorted(idx, [lo, lo + piece])
+        if b > a:
+            part = np.frombuffer(buf.read(min(piece, nbytes - lo), lo), dtype=np.uint8)
+            out[a:b] = part[idx[a:b] - lo]
+    return out
+
+
+def dump_outputs(out_dir, rank, world, nb, block, d_frames, d_ioff, d_ilen, d_out, d_olen, d_ost):
+    """What a caller of encode_dev + decode_dev receives from the last timed step, as float .npy
+    files (about 8 MiB; rank r > 0 of a multi-GPU run adds `.rank<r>` to the names):
+      frame_offsets, frame_lengths   float64[nb]  where the encoder put each frame, and its size
+      decode_lengths, decode_status  float64[nb]  bytes decoded per frame, S3HC_* status per frame
+      frames_sample                  float32      bytes of the packed frames at seeded positions
+      decoded_sample                 float32      bytes of the decoded output at seeded positions
+    Input and positions depend only on the arguments, so two builds compare array for array."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    fo = np.array(d_ioff.u64(nb), dtype=np.float64)
+    fl = np.array(d_ilen.u32(nb), dtype=np.float64)
+    comp = int(fo[-1] + fl[-1]) if nb else 0
+    arrays = {
+        "frame_offsets": fo,
+        "frame_lengths": fl,
+        "decode_lengths": np.array(d_olen.u32(nb), dtype=np.float64),
+        "decode_status": np.array(d_ost.i32(nb), dtype=np.float64),
+        "frames_sample": _sample_bytes(d_frames, min(comp, d_frames.numel()), 1),
+        "decoded_sample": _sample_bytes(d_out, nb * block, 2),
+    }
+    suffix = f".rank{rank}" if world > 1 and rank else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a)
+    return sorted(arrays)
 
 
 def run_rank(args):
@@ -453,7 +515,8 @@ def run_rank(args):
         step()
     sync_all()
     # correctness gate on the warmed-up state (outside the timed region)
-    if not args.skip_check:
+    check = args.full and not args.skip_check
+    if check:
         st = d_ost.i32(nb)
         assert st == [0] * nb, f"decode status {set(st)}"
         assert d_out.read(2 * block) == first_chunk[: 2 * block]
@@ -474,8 +537,12 @@ def run_rank(args):
     eng.set_timing(False)
     elapsed = g.max(t1 - t0)
     kt_timed = eng.timing()
+    dumped = None
+    if args.dump_outputs:
+        b = 0 if args.serial else (nstep[0] - 1) & 1  # the frame buffer the last timed step wrote
+        dumped = dump_outputs(args.dump_outputs, rank, world, nb, block, frames[b], ioffs[b], ilens[b], d_out, d_olen, d_ost)
     kt = {}
-    if not args.no_kernel_timing and args.profile_steps:
+    if args.full and not args.no_kernel_timing and args.profile_steps:
         eng.timing_reset()
         eng.set_timing(True)
         for _ in range(args.profile_steps):
@@ -486,7 +553,7 @@ def run_rank(args):
 
     # full-output check after the timed steps: every block, every byte, chunk by chunk
     checked = 0
-    if not args.skip_check:
+    if check:
         assert d_ost.i32(nb) == [0] * nb
         assert d_olen.u32(nb) == [block] * nb
         for c in range(nchunks):
@@ -509,6 +576,8 @@ def run_rank(args):
         "dec_close": nb * block,                  # U read (content xxh32 of every frame)
     }
     dom = max(excl, key=lambda k: excl[k][0] / excl[k][1]) if excl else None
+    if not args.full and "enc_parse" in kt_timed:
+        dom = "enc_parse"  # a plain run has no profiled steps: the one kernel its timed steps time by itself
     prof = nb == 4096 and not args.total_blocks
     # the dominant kernel's launch duration: from the timed steps' own events (enc_parse is timed
     # there), else from the profiled steps
@@ -520,7 +589,9 @@ def run_rank(args):
     # (compression.rs:479-480): the plan's device frame walk, the block decode and the content
     # xxh32 verify + EndMark checks, timed as one span in the timed steps ("dec_all"); the phase
     # breakdown and the block-decode kernels alone come from the profiled steps
-    roof_dec = roofline_whole_decode(kt, alg["decode"], prof, kt_timed.get("dec_all")) if "decode" in kt else None
+    roof_dec = None
+    if "decode" in kt or (not args.full and "dec_all" in kt_timed):
+        roof_dec = roofline_whole_decode(kt, alg["decode"], prof, kt_timed.get("dec_all"))
     roof_dec_k = roofline_obj(kt, "decode", alg["decode"], prof) if "decode" in kt else None
     per_kernel = {k: round(v[0] / v[1], 4) for k, v in kt.items()}
     rank_rate = nb * block * args.steps / (t1 - t0) / GiB
@@ -533,7 +604,7 @@ def run_rank(args):
         rates = [float(x[0].item()) for x in lst]
         devs = [int(x[1].item()) for x in lst]
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(first_chunk, block, args.cpu_seconds)
 
     if rank == 0:
@@ -562,9 +633,12 @@ def run_rank(args):
             },
             "per_gpu_gibps": [round(x, 3) for x in rates],
             "devices": {"visible": ndev, "rank_device": devs, "shared": len(set(devs)) < len(devs)},
+            "full": args.full,
+            "outputs_dumped": dumped,
             "blocks_checked": int(checked_all),
-            "kernel_ms_per_step": per_kernel,
-            "kernel_ms_source": f"{args.profile_steps} steps after the timed ones, every phase its own event pair",
+            "kernel_ms_per_step": per_kernel if args.full else None,
+            "kernel_ms_source": (f"{args.profile_steps} steps after the timed ones, every phase its own event pair"
+                                 if args.full else "not measured: --full times every phase"),
             "roofline": roof,
             "roofline_decode": roof_dec,
             "roofline_decode_kernels": roof_dec_k,

@@ -4,8 +4,8 @@
 OTHER=$1; N=${2:-2}; O=${3:-gpurun_out/ab}
 mkdir -p $O
 for i in $(seq 1 $N); do
-  timeout -k 10 200 python -u bench.py --no-cpu-baseline > $O/tree_$i.json 2> $O/tree_$i.err || exit 1
-  S3HC_LIB_PATH=$OTHER timeout -k 10 200 python -u bench.py --no-cpu-baseline > $O/other_$i.json 2> $O/other_$i.err || exit 1
+  timeout -k 10 200 python -u bench.py --full --no-cpu-baseline > $O/tree_$i.json 2> $O/tree_$i.err || exit 1
+  S3HC_LIB_PATH=$OTHER timeout -k 10 200 python -u bench.py --full --no-cpu-baseline > $O/other_$i.json 2> $O/other_$i.err || exit 1
 done
 python3 - "$O" "$N" <<'PY'
 import json, sys
