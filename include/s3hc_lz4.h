@@ -322,6 +322,78 @@ void s3hc_writer_abort(s3hc_writer* w);
 /* Message of the last failing writer/aggregator call on this thread. */
 const char* s3hc_writer_last_error(void);
 
+/* ---- seekable range files: frame index, size scan, sliced read -------------- */
+/* No reference counterpart: a request for a sub-range of a cached range is refused by
+ * stream_range_data (http_proxy.rs:7931-7958) and served by the buffered path, which reads the
+ * whole range file, decodes all of it (disk_cache.rs:3470-3610 -> decompress_data,
+ * compression.rs:463-502) and then slices (http_proxy.rs:8797-8826, range_handler.rs:1203-1283).
+ * An s3hc_index describes one range file as a chain of frames, one entry per frame:
+ * {c_off, u_off, c_len, u_len} = where the frame starts in the file and in the decoded bytes
+ * (exclusive prefix sums) and how long it is in each. It follows decompress_data: it ends
+ * before the first frame that yields 0 bytes (compression.rs:463-502, Ok(0) => break); later
+ * bytes are not indexed. With it, a read of decoded bytes [lo, hi) reads and decodes only the
+ * frames that hold them. The index functions are host code and set no s3hc_last_error message. */
+typedef struct s3hc_index s3hc_index;
+/* Builds the offsets itself. n = 0 is an empty index. A zero c_len or an offset beyond 64 bits
+ * is S3HC_INVALID_ARG. */
+int s3hc_index_from_entries(const uint32_t* c_len, const uint32_t* u_len, uint32_t n, s3hc_index** out);
+void s3hc_index_free(s3hc_index* idx);
+uint32_t s3hc_index_count(const s3hc_index* idx);
+/* out = {c_off, u_off, c_len, u_len} of frame i. */
+int s3hc_index_entry(const s3hc_index* idx, uint32_t i, uint64_t out[4]);
+int s3hc_index_total(const s3hc_index* idx, uint64_t* c_total, uint64_t* u_total);
+/* The frames [first, first + count) that hold decoded bytes [lo, hi), and the compressed bytes
+ * [c_off, c_off + c_len) of the file the caller has to read for them (binary search, host).
+ * lo > hi or hi > u_total: S3HC_INVALID_ARG. lo == hi: count = 0. */
+int s3hc_index_span(const s3hc_index* idx, uint64_t lo, uint64_t hi, uint32_t* first, uint32_t* count,
+                    uint64_t* c_off, uint64_t* c_len);
+/* Side-car form (INTEGRATION.md "Seek index"): "S3HCIDX", a version byte, the entry count, the
+ * c_len / u_len pairs (u32 little-endian), a trailing xxh32 of everything before it.
+ * s3hc_index_load returns S3HC_CORRUPT for a bad magic or version, truncation or trailing bytes,
+ * a count that does not match the length, a checksum mismatch or a zero c_len; it sizes nothing
+ * by the count before the count has been checked against the length. */
+size_t s3hc_index_serialized_size(const s3hc_index* idx);
+int s3hc_index_serialize(const s3hc_index* idx, uint8_t* dst, size_t cap, size_t* n);
+int s3hc_index_load(const uint8_t* src, size_t n, s3hc_index** out);
+
+/* s3hc_writer_commit (finalize_incremental_range, disk_cache.rs:1968-2090) plus the index of the
+ * frames this writer delivered to its sink, in order: one entry per frame under every frame
+ * policy (S3HC_BLK_64K_PER_FRAME: one per 64 KiB of a batch), store-mode writers and multi-device
+ * aggregators included. *idx is NULL on failure. Frees w. */
+int s3hc_writer_commit_indexed(s3hc_writer* w, double min_commit_ratio, uint64_t spec_out[4], s3hc_index** idx);
+
+/* The size scan, for files that have no side-car (every file the reference wrote, liblz4 frames):
+ * the decoded length of frame i = d_src[frame_off[i] .. +frame_len[i]) into d_u_len[i], its
+ * status into d_status[i] (device arrays; frame tables are host arrays), from the token chains
+ * alone: no decoded byte, token or sequence record is written. A frame that s3hc_decode_dev
+ * decodes S3HC_OK scans S3HC_OK with the same length. S3HC_CORRUPT: a malformed header, a token
+ * chain that runs off its block, a block larger than the frame's block maximum, a content-size
+ * field that differs, a frame total above 4 GiB - 1. The scan does not see checksum faults or bad
+ * match offsets: those surface at the sliced read, which always decodes and verifies. It reads
+ * nothing outside [frame_off, frame_off + frame_len). Returns after the results are written. */
+int s3hc_frame_sizes_dev(s3hc_ctx* ctx, const uint8_t* d_src, const uint64_t* frame_off,
+                         const uint32_t* frame_len, uint32_t n, uint32_t* d_u_len, int32_t* d_status,
+                         void* stream);
+/* The index of a range file in a host buffer: the frame walk of s3hc_decompress_frames, then the
+ * size scan over the uploaded frames, in passes of about 256 MiB of compressed bytes. Any fault
+ * the walk or the scan sees before the index's end fails the call, as it fails decompress_data. */
+int s3hc_index_build(s3hc_ctx* ctx, const uint8_t* src, size_t n, s3hc_index** out);
+
+/* The sliced read: decoded bytes [lo, hi) of the file into dst. first / count and span = the
+ * span_len compressed bytes that s3hc_index_span named for [lo, hi) (a wider run of frames that
+ * holds [lo, hi) works too). Exactly those frames are decoded (output slots packed by the index's
+ * sizes), their block and content checksums verified, each decoded length checked against the
+ * index, and only [lo, hi) is copied back. On success the bytes equal decompress_data(file)[lo..hi].
+ * A length that differs from the index, or a span that does not parse as exactly those frames, is
+ * S3HC_CORRUPT with the message "stale index". On any fault no bytes are returned and the first
+ * fault in stream order decides the status (the caller treats it as a cache miss).
+ * The one knowing difference from the buffered path: a fault in a frame the slice does not touch
+ * is not seen. cap < hi - lo: S3HC_DST_TOO_SMALL. lo == hi: S3HC_OK, 0 bytes, no GPU work.
+ * A slice is decoded in one pass: device scratch follows the touched frames' decoded size. */
+int s3hc_decompress_slice(s3hc_ctx* ctx, const s3hc_index* idx, uint32_t first, uint32_t count,
+                          const uint8_t* span, size_t span_len, uint64_t lo, uint64_t hi, uint8_t* dst,
+                          size_t cap, size_t* out_len);
+
 #ifdef __cplusplus
 }
 #endif

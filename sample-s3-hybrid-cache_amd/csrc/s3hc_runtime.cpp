@@ -26,6 +26,7 @@
 #include "s3hc_lz4_diag.h"
 #include "s3hc_plan.hpp"
 #include "s3hc_guard.hpp"
+#include "s3hc_index.hpp"
 #include "s3hc_knobs.hpp"
 
 namespace s3hc {
@@ -69,6 +70,8 @@ hipError_t launch_dframe_close(const uint8_t*, const uint64_t*, const uint64_t*,
                                const uint32_t*, const int32_t*, const uint64_t*, const uint8_t*, const uint64_t*,
                                const uint32_t*, uint32_t, const int32_t*, int32_t*, uint32_t*, uint32_t*, hipStream_t,
                                uint32_t* pend = nullptr);
+hipError_t launch_frame_sizes(const uint8_t*, const uint64_t*, const uint32_t*, uint32_t, uint32_t*, int32_t*,
+                              hipStream_t);
 }  // namespace s3hc
 
 using namespace s3hc;
@@ -658,6 +661,7 @@ struct s3hc_ctx {
     DevBuf d_blocks, d_units, d_blk_out, d_blk_status, d_rng_off, d_rng_len, d_hash;
     DevBuf d_c_soff, d_c_len, d_c_doff, d_c_hash, d_c_flen;  // compat encoder descriptors
     DevBuf d_ftab, d_fstat, d_flen, d_fhash;                  // per-frame tables of decode_walk
+    DevBuf d_ix_off, d_ix_len, d_ix_ulen, d_ix_stat;          // frame tables and results of the size scan
     HostStage hs;
     LbScratch lb;
     // range-reader resources kept warm between the readers of this context (s3hc_reader_*): one
@@ -1476,9 +1480,15 @@ extern "C" int s3hc_decompressed_bound(const uint8_t* src, size_t n, size_t* bou
 static double host_us() {
     return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
+// A sliced read (s3hc_decompress_slice): every frame must decode to the length its index entry
+// names, and only bytes [lo, hi) of the frames' concatenated output are delivered.
+struct SliceReq {
+    const uint32_t* want_len;  // per frame of the walk
+    uint64_t lo, hi;
+};
 static int decode_walk(s3hc_ctx* ctx, const uint8_t* src, size_t n, HWalk& W, bool stream_mode,
                        std::vector<uint8_t>* vout, uint8_t* dst, size_t cap, size_t* out_len,
-                       bool upload_in = true, bool* stopped_out = nullptr) {
+                       bool upload_in = true, bool* stopped_out = nullptr, const SliceReq* slice = nullptr) {
     const bool trace = knob_on(KN_HOST_TRACE);  // diagnostics: stage times
     const double t_0 = trace ? host_us() : 0.0;
 #define HTRACE(tag) if (trace) fprintf(stderr, "[s3hc host] %-10s %8.1f us\n", tag, host_us() - t_0);
@@ -1579,7 +1589,8 @@ static int decode_walk(s3hc_ctx* ctx, const uint8_t* src, size_t n, HWalk& W, bo
                 spos[f] = stot;
                 stot += spre[f];
             }
-            spec = stot <= kSpecBytes && (vout || !host_pinned(dst));
+            // (a sliced read copies back [lo, hi) alone, once the frames are verified)
+            spec = !slice && stot <= kSpecBytes && (vout || !host_pinned(dst));
             if (spec && stot) {
                 HIPCHK(hs.init(stot));
                 HIPCHK(hs.buf[0].ensure(stot + 16));
@@ -1611,6 +1622,7 @@ static int decode_walk(s3hc_ctx* ctx, const uint8_t* src, size_t n, HWalk& W, bo
     int err_status = S3HC_OK;
     size_t use_frames = nf;    // frames whose output is delivered / checksummed
     bool stopped = false;
+    bool stale = false;        // sliced read: a frame is not the one its index entry describes
     std::vector<uint64_t> fout(nf, 0);
     bool need_compact = false;
     for (size_t f = 0; f < nf; ++f) {
@@ -1624,11 +1636,17 @@ static int decode_walk(s3hc_ctx* ctx, const uint8_t* src, size_t n, HWalk& W, bo
             if (bs[b] < S3HC_OK || bs[b] > S3HC_INVALID_ARG || (bs[b] == S3HC_OK && bo[b] > W.blocks[b].limit))
                 return fail(S3HC_DEVICE, "decode results out of range");
             if (W.blk_has_cs[b] && cs_got[b] != W.blk_cs_want[b]) { fs = S3HC_CHECKSUM; break; }
-            if (bs[b] != S3HC_OK) { fs = bs[b]; break; }
+            if (bs[b] != S3HC_OK) {
+                // (a single-block frame's room is its index length: more bytes = not that frame)
+                fs = bs[b];
+                if (slice && fs == S3HC_DST_TOO_SMALL) { fs = S3HC_CORRUPT; stale = true; }
+                break;
+            }
             if ((F.flg & 0x20) && k + 1 < F.nblk && bo[b] != W.blocks[b].cap) need_compact = true;
             tot += bo[b];
         }
         if (fs == S3HC_OK && f + 1 == nf && W.last_incomplete) fs = W.tail_status;  // incomplete frame
+        if (fs == S3HC_OK && slice && tot != slice->want_len[f]) { fs = S3HC_CORRUPT; stale = true; }
         if (fs != S3HC_OK) { err_status = fs; use_frames = f; break; }
         fout[f] = tot;
         if (!stream_mode && tot == 0) { use_frames = f + 1; stopped = true; break; }
@@ -1704,9 +1722,27 @@ static int decode_walk(s3hc_ctx* ctx, const uint8_t* src, size_t n, HWalk& W, bo
         }
     }
     HTRACE("resolved")
-    if (err_status != S3HC_OK) return fail(err_status, "frame decode failed");
+    if (err_status != S3HC_OK) return fail(err_status, stale ? "stale index" : "frame decode failed");
     // Deliver
     uint8_t* hdst = dst;
+    if (slice) {
+        // bytes [lo, hi) of the frames' concatenated output, from wherever each frame's lies
+        std::vector<std::pair<const uint8_t*, uint64_t>> sruns;
+        uint64_t at = 0;
+        for (size_t f = 0; f < use_frames; ++f) {
+            const uint64_t a = std::max<uint64_t>(at, slice->lo), b = std::min<uint64_t>(at + fout[f], slice->hi);
+            if (a < b) {
+                const uint8_t* from = dev_out + fpos[f] + (a - at);
+                if (!sruns.empty() && sruns.back().first + sruns.back().second == from) sruns.back().second += b - a;
+                else sruns.push_back({from, b - a});
+            }
+            at += fout[f];
+        }
+        if (slice->hi > at || slice->hi - slice->lo > cap) return fail(S3HC_INVALID_ARG, "slice outside the decoded frames");
+        HIPCHK(hs.d2h(hdst, sruns, st));
+        if (out_len) *out_len = (size_t)(slice->hi - slice->lo);
+        return S3HC_OK;
+    }
     if (vout) {
         size_t o0 = vout->size();
         vout->resize(o0 + total);
@@ -1865,6 +1901,146 @@ extern "C" int s3hc_decompress_frames_alloc(s3hc_ctx* ctx, const uint8_t* src, s
     });
 }
 extern "C" void s3hc_buffer_free(uint8_t* p) { free(p); }
+
+// ------------------------------------------- seekable range files
+// The size scan of n frames of d_src (frame tables on the host); caller holds ctx->mu. Results are
+// on the device when the stream reaches the end of the launch.
+static int frame_sizes_locked(s3hc_ctx* ctx, const uint8_t* d_src, const uint64_t* frame_off, const uint32_t* frame_len,
+                              uint32_t n, uint32_t* d_u_len, int32_t* d_status, hipStream_t st) {
+    std::vector<uint64_t> fo(frame_off, frame_off + n);
+    std::vector<uint32_t> fl(frame_len, frame_len + n);
+    HIPCHK(upload(ctx->d_ix_off, fo, st));
+    HIPCHK(upload(ctx->d_ix_len, fl, st));
+    KTimer T(ctx, st);
+    T.begin("size_scan");
+    HIPCHK(launch_frame_sizes(d_src, ctx->d_ix_off.as<uint64_t>(), ctx->d_ix_len.as<uint32_t>(), n, d_u_len, d_status, st));
+    T.end();
+    HIPCHK(hipStreamSynchronize(st));  // (the frame tables belong to the context: one scan at a time)
+    return S3HC_OK;
+}
+
+extern "C" int s3hc_frame_sizes_dev(s3hc_ctx* ctx, const uint8_t* d_src, const uint64_t* frame_off,
+                                    const uint32_t* frame_len, uint32_t n, uint32_t* d_u_len, int32_t* d_status,
+                                    void* stream) {
+    return guarded([&]() -> int {
+        if (!ctx || (n && (!d_src || !frame_off || !frame_len || !d_u_len || !d_status)))
+            return fail(S3HC_INVALID_ARG, "bad arguments");
+        if (!n) return S3HC_OK;
+        std::lock_guard<std::mutex> g(ctx->mu);
+        HIPCHK(hipSetDevice(ctx->device));
+        return frame_sizes_locked(ctx, d_src, frame_off, frame_len, n, d_u_len, d_status,
+                                  stream ? (hipStream_t)stream : ctx->stream);
+    });
+}
+
+// Compressed bytes uploaded per pass of s3hc_index_build (a larger frame is a pass of its own).
+static constexpr uint64_t kIndexPassBytes = 256ull << 20;
+
+extern "C" int s3hc_index_build(s3hc_ctx* ctx, const uint8_t* src, size_t n, s3hc_index** out) {
+    if (!ctx || (!src && n) || !out) return fail(S3HC_INVALID_ARG, "bad arguments");
+    *out = nullptr;
+    return guarded([&]() -> int {
+        std::lock_guard<std::mutex> g(ctx->mu);
+        HIPCHK(hipSetDevice(ctx->device));
+        hipStream_t st = ctx->stream;
+        // decompress_data's walk (compression.rs:474-494): a structural fault anywhere before an
+        // empty frame fails the whole read, so there is nothing to index
+        HWalk W;
+        walk_frames(src, n, W, false, true);
+        if (W.tail_status != S3HC_OK) return fail(W.tail_status, "frame walk failed");
+        size_t nf = W.frames.size();
+        if (nf && W.frames[nf - 1].nblk == 0) --nf;  // the empty frame that ended the walk
+        std::vector<uint32_t> c_len, u_len;
+        bool ended = false;
+        for (size_t a = 0; a < nf && !ended;) {
+            size_t b = a;
+            uint64_t bytes = 0;
+            std::vector<uint64_t> fo;
+            std::vector<uint32_t> fl;
+            const size_t base = W.frames[a].pos;
+            while (b < nf) {
+                const uint64_t len = (b + 1 < W.frames.size() ? W.frames[b + 1].pos : W.end) - W.frames[b].pos;
+                if (len > 0xFFFFFFFFull) return fail(S3HC_UNSUPPORTED, "a frame of 4 GiB or more");
+                if (b > a && bytes + len > kIndexPassBytes) break;
+                fo.push_back(W.frames[b].pos - base);
+                fl.push_back((uint32_t)len);
+                bytes += len;
+                ++b;
+            }
+            const uint32_t k = (uint32_t)(b - a);
+            HIPCHK(ctx->d_in.ensure(bytes + 64));
+            HIPCHK(ctx->hs.h2d(ctx->d_in.p, src + base, bytes, st));
+            HIPCHK(ctx->d_ix_ulen.ensure((size_t)k * 4));
+            HIPCHK(ctx->d_ix_stat.ensure((size_t)k * 4));
+            if (int rc = frame_sizes_locked(ctx, ctx->d_in.as<uint8_t>(), fo.data(), fl.data(), k,
+                                            ctx->d_ix_ulen.as<uint32_t>(), ctx->d_ix_stat.as<int32_t>(), st))
+                return rc;
+            std::vector<uint32_t> ul(k);
+            std::vector<int32_t> fs(k);
+            HIPCHK(hipMemcpy(ul.data(), ctx->d_ix_ulen.p, (size_t)k * 4, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(fs.data(), ctx->d_ix_stat.p, (size_t)k * 4, hipMemcpyDeviceToHost));
+            for (uint32_t i = 0; i < k; ++i) {
+                if (fs[i] < S3HC_OK || fs[i] > S3HC_INVALID_ARG) return fail(S3HC_DEVICE, "scan results out of range");
+                if (fs[i] != S3HC_OK) return fail(fs[i], "frame size scan failed");
+                if (ul[i] == 0) {  // a frame yielding no bytes ends the read (Ok(0) => break)
+                    ended = true;
+                    break;
+                }
+                c_len.push_back(fl[i]);
+                u_len.push_back(ul[i]);
+            }
+            a = b;
+        }
+        int rc;
+        *out = s3hc::index_make(c_len.data(), u_len.data(), (uint32_t)c_len.size(), &rc);
+        return rc ? fail(rc, "frame index") : S3HC_OK;
+    });
+}
+
+extern "C" int s3hc_decompress_slice(s3hc_ctx* ctx, const s3hc_index* idx, uint32_t first, uint32_t count,
+                                     const uint8_t* span, size_t span_len, uint64_t lo, uint64_t hi, uint8_t* dst,
+                                     size_t cap, size_t* out_len) {
+    if (!ctx || !idx || !out_len || lo > hi) return fail(S3HC_INVALID_ARG, "bad arguments");
+    *out_len = 0;
+    if (lo == hi) return S3HC_OK;  // (an empty slice names no frame: no GPU work)
+    const size_t nidx = idx->c_len.size();
+    if (first > nidx || count > nidx - first) return fail(S3HC_INVALID_ARG, "frames outside the index");
+    if (lo < idx->u_off[first] || hi > idx->u_off[first + count])
+        return fail(S3HC_INVALID_ARG, "slice outside the named frames");
+    if (hi - lo > cap) return fail(S3HC_DST_TOO_SMALL, "dst capacity below the slice");
+    if ((!span && span_len) || !dst) return fail(S3HC_INVALID_ARG, "bad arguments");
+    return guarded([&]() -> int {
+        std::lock_guard<std::mutex> g(ctx->mu);
+        HIPCHK(hipSetDevice(ctx->device));
+        // the span must be exactly the frames the index names
+        if (span_len != idx->c_off[first + count] - idx->c_off[first]) return fail(S3HC_CORRUPT, "stale index");
+        HWalk W;
+        walk_frames(span, span_len, W, false, false);
+        if (W.tail_status != S3HC_OK || W.frames.size() != count || W.end != span_len)
+            return fail(S3HC_CORRUPT, "stale index");
+        for (uint32_t i = 0; i < count; ++i)
+            if (W.frames[i].pos != idx->c_off[first + i] - idx->c_off[first]) return fail(S3HC_CORRUPT, "stale index");
+        // output slots packed by the index: a single-block frame gets exactly its decoded length
+        // (frames of several blocks keep the walk's per-block bounds)
+        uint64_t off = 0;
+        for (uint32_t i = 0; i < count; ++i) {
+            HFrame& F = W.frames[i];
+            F.out_off = off;
+            uint64_t slot = 0;
+            for (uint32_t k = 0; k < F.nblk; ++k) {
+                DecBlock& D = W.blocks[F.blk0 + k];
+                if (F.nblk == 1) D.cap = std::min(D.cap, idx->u_len[first + i]);
+                D.dst_off = off + slot;
+                slot += D.cap;
+            }
+            off += slot;
+        }
+        W.slot_total = off;
+        const uint64_t u0 = idx->u_off[first];
+        const SliceReq R{idx->u_len.data() + first, lo - u0, hi - u0};
+        return decode_walk(ctx, span, span_len, W, false, nullptr, dst, cap, out_len, true, nullptr, &R);
+    });
+}
 
 // ------------------------------------------------------ streaming decoder
 struct s3hc_stream {

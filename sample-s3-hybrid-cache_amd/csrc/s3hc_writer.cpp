@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "s3hc_guard.hpp"
+#include "s3hc_index.hpp"
 #include "s3hc_lz4.h"
 
 namespace {
@@ -125,6 +126,7 @@ struct s3hc_writer {
     uint64_t bytes_written = 0;             // every chunk (uncompressed)
     uint64_t compressed_bytes_written = 0;  // delivered frames
     uint32_t queued = 0;                    // batches queued and not yet delivered
+    std::vector<uint32_t> idx_c, idx_u;     // per delivered frame: framed / input bytes (s3hc_writer_commit_indexed)
     std::atomic<int> error{S3HC_OK};        // sticky: first failure of a queued batch (set under agg->mu)
     std::string error_msg;                  // guarded by agg->mu
 };
@@ -269,6 +271,41 @@ static int encode_shard(const s3hc_aggregator* a, Lane& Ln, const std::deque<Bat
     return S3HC_OK;
 }
 
+// The frames of one delivered batch, for the writer's index: a batch is one frame, except under
+// S3HC_BLK_64K_PER_FRAME (plan mode 2), where it is one frame per 64 KiB of input. Their framed
+// lengths come from a walk of the block words (each frame: header, blocks, EndMark, checksum).
+static bool record_frames(s3hc_writer* w, uint8_t mode, const uint8_t* fr, uint32_t flen, uint64_t blen) {
+    if (mode != 2) {
+        w->idx_c.push_back(flen);
+        w->idx_u.push_back((uint32_t)blen);
+        return true;
+    }
+    auto rd32 = [](const uint8_t* p) {
+        return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+    };
+    uint64_t pos = 0, u = 0;
+    while (pos < flen) {
+        if (flen - pos < 7 || u >= blen) return false;
+        const uint32_t flg = fr[pos + 4];
+        uint64_t ip = pos + 7 + ((flg & 0x08) ? 8 : 0) + ((flg & 0x01) ? 4 : 0);
+        for (;;) {
+            if (ip + 4 > flen) return false;
+            const uint32_t bw = rd32(fr + ip);
+            ip += 4;
+            if (bw == 0) break;
+            ip += (uint64_t)(bw & 0x7FFFFFFFu) + ((flg & 0x10) ? 4 : 0);
+        }
+        ip += (flg & 0x04) ? 4 : 0;
+        if (ip > flen) return false;
+        const uint64_t ul = std::min<uint64_t>(65536, blen - u);
+        w->idx_c.push_back((uint32_t)(ip - pos));
+        w->idx_u.push_back((uint32_t)ul);
+        u += ul;
+        pos = ip;
+    }
+    return u == blen;
+}
+
 // Encode every queued batch (one launch per device: contiguous shards over the aggregator's
 // lanes, run concurrently) and deliver the frames in queue order. Caller holds flush_mu.
 static int aggregated_flush(s3hc_aggregator* a) {
@@ -352,13 +389,15 @@ static int aggregated_flush(s3hc_aggregator* a) {
         if (!w->error.load(std::memory_order_acquire) && fr) {
             if (w->sink && w->sink(w->user, fr, flen[i]) != 0) {
                 src = S3HC_INVALID_ARG;
+            } else if (!record_frames(w, work[i].mode, fr, flen[i], blen[i])) {
+                src = S3HC_CORRUPT;
             } else {
                 w->compressed_bytes_written += flen[i];
                 if (a->stats) s3hc_handler_record_batch_bytes(a->stats, blen[i], flen[i]);
             }
         }
         std::lock_guard<std::mutex> g(a->mu);
-        if (src) set_writer_error(w, src, "frame sink failed (write_all)");
+        if (src) set_writer_error(w, src, src == S3HC_CORRUPT ? "delivered frames do not parse" : "frame sink failed (write_all)");
         w->queued--;
     }
     return first_rc ? werr(first_rc, first_msg) : S3HC_OK;
@@ -574,7 +613,7 @@ struct WriterReaper {
     }
 };
 
-extern "C" int s3hc_writer_commit(s3hc_writer* w, double min_commit_ratio, uint64_t spec_out[4]) {
+static int writer_commit(s3hc_writer* w, double min_commit_ratio, uint64_t spec_out[4], s3hc_index** idx_out) {
     if (!w) return werr(S3HC_INVALID_ARG, "bad arguments");
     WriterReaper reaper{w};
     return guarded([&]() -> int {
@@ -603,6 +642,15 @@ extern "C" int s3hc_writer_commit(s3hc_writer* w, double min_commit_ratio, uint6
             }
             end = w->start + w->bytes_written - 1;
         }
+        if (idx_out) {  // the frames this writer's sink received, in order
+            int irc;
+            *idx_out = s3hc::index_make(w->idx_c.data(), w->idx_u.data(), (uint32_t)w->idx_c.size(), &irc);
+            if (irc) {
+                reaper.w = nullptr;
+                delete w;
+                return werr(irc, "frame index");
+            }
+        }
         if (w->agg->stats) s3hc_handler_record_object(w->agg->stats, w->compression_enabled ? 1 : 0);  // :2053
         if (spec_out) {  // RangeSpec::new(start, end, path, Lz4, compressed, uncompressed) (disk_cache.rs:2080-2087)
             spec_out[0] = w->start;
@@ -614,6 +662,20 @@ extern "C" int s3hc_writer_commit(s3hc_writer* w, double min_commit_ratio, uint6
         delete w;
         return S3HC_OK;
     });
+}
+
+extern "C" int s3hc_writer_commit(s3hc_writer* w, double min_commit_ratio, uint64_t spec_out[4]) {
+    return writer_commit(w, min_commit_ratio, spec_out, nullptr);
+}
+
+extern "C" int s3hc_writer_commit_indexed(s3hc_writer* w, double min_commit_ratio, uint64_t spec_out[4],
+                                          s3hc_index** idx) {
+    if (!idx) {
+        s3hc_writer_abort(w);
+        return werr(S3HC_INVALID_ARG, "bad arguments");
+    }
+    *idx = nullptr;
+    return writer_commit(w, min_commit_ratio, spec_out, idx);
 }
 
 extern "C" void s3hc_writer_abort(s3hc_writer* w) {

@@ -142,6 +142,20 @@ def _load():
         "s3hc_writer_commit": (i32, [vp, ctypes.c_double, ctypes.POINTER(u64)]),
         "s3hc_writer_abort": (None, [vp]),
         "s3hc_writer_last_error": (ctypes.c_char_p, []),
+        "s3hc_writer_commit_indexed": (i32, [vp, ctypes.c_double, ctypes.POINTER(u64), ctypes.POINTER(vp)]),
+        "s3hc_index_from_entries": (i32, [ctypes.POINTER(u32), ctypes.POINTER(u32), u32, ctypes.POINTER(vp)]),
+        "s3hc_index_free": (None, [vp]),
+        "s3hc_index_count": (u32, [vp]),
+        "s3hc_index_entry": (i32, [vp, u32, ctypes.POINTER(u64)]),
+        "s3hc_index_total": (i32, [vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
+        "s3hc_index_span": (i32, [vp, u64, u64, ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(u64),
+                                  ctypes.POINTER(u64)]),
+        "s3hc_index_serialized_size": (sz, [vp]),
+        "s3hc_index_serialize": (i32, [vp, u8p, sz, szp]),
+        "s3hc_index_load": (i32, [u8p, sz, ctypes.POINTER(vp)]),
+        "s3hc_frame_sizes_dev": (i32, [vp, vp, vp, vp, u32, vp, vp, vp]),
+        "s3hc_index_build": (i32, [vp, u8p, sz, ctypes.POINTER(vp)]),
+        "s3hc_decompress_slice": (i32, [vp, vp, u32, u32, u8p, sz, u64, u64, u8p, sz, szp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -255,6 +269,85 @@ def frame_bound(n: int) -> int:
     return lib.s3hc_frame_bound(n)
 
 
+class FrameIndex:
+    """s3hc_index: one entry {c_off, u_off, c_len, u_len} per frame of a range file, as far as
+    decompress_data reads it (compression.rs:463-502). Host data; needs no GPU."""
+
+    def __init__(self, h):
+        self.h = h
+
+    @classmethod
+    def from_entries(cls, c_len, u_len) -> "FrameIndex":
+        n = len(c_len)
+        assert len(u_len) == n
+        h = ctypes.c_void_p()
+        rc = lib.s3hc_index_from_entries((ctypes.c_uint32 * max(n, 1))(*c_len), (ctypes.c_uint32 * max(n, 1))(*u_len),
+                                         n, ctypes.byref(h))
+        if rc != S3HC_OK:
+            raise CodecError(rc, "s3hc_index_from_entries")
+        return cls(h)
+
+    @classmethod
+    def from_bytes(cls, blob) -> "FrameIndex":
+        p, keep = _ptr(blob)
+        h = ctypes.c_void_p()
+        rc = lib.s3hc_index_load(p, len(keep), ctypes.byref(h))
+        if rc != S3HC_OK:
+            raise CodecError(rc, "s3hc_index_load")
+        return cls(h)
+
+    def to_bytes(self) -> bytes:
+        cap = lib.s3hc_index_serialized_size(self.h)
+        out = ctypes.create_string_buffer(cap)
+        n = ctypes.c_size_t()
+        rc = lib.s3hc_index_serialize(self.h, out, cap, ctypes.byref(n))
+        if rc != S3HC_OK:
+            raise CodecError(rc, "s3hc_index_serialize")
+        return out.raw[: n.value]
+
+    def __len__(self) -> int:
+        return lib.s3hc_index_count(self.h)
+
+    @property
+    def entries(self) -> list:
+        """[(c_off, u_off, c_len, u_len)] per frame."""
+        out, e = [], (ctypes.c_uint64 * 4)()
+        for i in range(len(self)):
+            rc = lib.s3hc_index_entry(self.h, i, e)
+            if rc != S3HC_OK:
+                raise CodecError(rc, "s3hc_index_entry")
+            out.append(tuple(e))
+        return out
+
+    @property
+    def total(self) -> tuple:
+        """(compressed bytes, decoded bytes) the index covers."""
+        c, u = ctypes.c_uint64(), ctypes.c_uint64()
+        lib.s3hc_index_total(self.h, ctypes.byref(c), ctypes.byref(u))
+        return c.value, u.value
+
+    def span(self, lo: int, hi: int) -> tuple:
+        """(first, count, c_off, c_len): the frames holding decoded bytes [lo, hi) and the bytes of
+        the file to read for them."""
+        f, k = ctypes.c_uint32(), ctypes.c_uint32()
+        o, n = ctypes.c_uint64(), ctypes.c_uint64()
+        rc = lib.s3hc_index_span(self.h, lo, hi, ctypes.byref(f), ctypes.byref(k), ctypes.byref(o), ctypes.byref(n))
+        if rc != S3HC_OK:
+            raise CodecError(rc, "s3hc_index_span")
+        return f.value, k.value, o.value, n.value
+
+    def __eq__(self, other):
+        return isinstance(other, FrameIndex) and self.entries == other.entries
+
+    def __del__(self):
+        try:
+            if self.h:
+                lib.s3hc_index_free(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+
 class Engine:
     """One s3hc context on one GPU."""
 
@@ -314,6 +407,39 @@ class Engine:
     def stream(self) -> "FrameStream":
         return FrameStream(self)
 
+    # ---- seekable range files: frame index, size scan, sliced read
+    def build_index(self, data) -> FrameIndex:
+        """The index of a range file that has no side-car (header walk + size scan on the GPU)."""
+        p, keep = _ptr(data)
+        h = ctypes.c_void_p()
+        _check(lib.s3hc_index_build(self.h, p, len(keep), ctypes.byref(h)))
+        return FrameIndex(h)
+
+    def frame_sizes_dev(self, d_src, frame_off, frame_len, d_u_len, d_status, stream=None):
+        """Decoded length and status of every frame of d_src into the device arrays (no decode)."""
+        n = len(frame_off)
+        _check(lib.s3hc_frame_sizes_dev(self.h, d_src.data_ptr(), (ctypes.c_uint64 * max(n, 1))(*frame_off),
+                                        (ctypes.c_uint32 * max(n, 1))(*frame_len), n, d_u_len.data_ptr(),
+                                        d_status.data_ptr(), _q(stream)))
+
+    def read_slice(self, index: FrameIndex, span_bytes, lo: int, hi: int, cap: int | None = None,
+                   first: int | None = None, count: int | None = None) -> bytes:
+        """Decoded bytes [lo, hi) from the compressed bytes index.span(lo, hi) named (first / count:
+        the frames span_bytes holds when they are not span(lo, hi)'s)."""
+        if first is None:
+            first, count = index.span(lo, hi)[:2]
+        p, keep = _ptr(span_bytes)
+        cap = hi - lo if cap is None else cap
+        out = ctypes.create_string_buffer(max(cap, 1))
+        n = ctypes.c_size_t()
+        _check(lib.s3hc_decompress_slice(self.h, index.h, first, count, p, len(keep), lo, hi, out, cap, ctypes.byref(n)))
+        return out.raw[: n.value]
+
+    def read_range(self, file_bytes, index: FrameIndex, lo: int, hi: int) -> bytes:
+        """span + slice in one call, for a file already in memory."""
+        first, count, c_off, c_len = index.span(lo, hi)
+        return self.read_slice(index, bytes(file_bytes[c_off:c_off + c_len]), lo, hi, first=first, count=count)
+
     # ---- match-finder mode of this engine's encodes (frames decode the same either way)
     def set_encode_mode(self, mode: int):
         _check(lib.s3hc_set_encode_mode(self.h, mode))
@@ -335,7 +461,7 @@ class Engine:
         _check(lib.s3hc_timing_collect(self.h))
         out = {}
         for name in ("xxh32_side", "xxh32", "enc_parse", "enc_sizes", "enc_emit", "dec_plan", "decode", "dec_finish", "dec_close",
-                     "dec_all", "compat"):
+                     "dec_all", "compat", "size_scan"):
             n = lib.s3hc_kernel_count(self.h, name.encode())
             if n:
                 out[name] = (lib.s3hc_last_kernel_ms(self.h, name.encode()), n)
@@ -860,6 +986,15 @@ class IncrementalRangeWriter:
         h, self.h = self.h, None
         _wcheck(lib.s3hc_writer_commit(h, -1.0 if min_commit_ratio is None else min_commit_ratio, spec))
         return RangeSpec(*list(spec))
+
+    def commit_indexed(self, min_commit_ratio: float | None = None) -> tuple:
+        """commit() plus the FrameIndex of the frames the sink received."""
+        spec = (ctypes.c_uint64 * 4)()
+        idx = ctypes.c_void_p()
+        h, self.h = self.h, None
+        _wcheck(lib.s3hc_writer_commit_indexed(h, -1.0 if min_commit_ratio is None else min_commit_ratio, spec,
+                                               ctypes.byref(idx)))
+        return RangeSpec(*list(spec)), FrameIndex(idx)
 
     def abort(self):
         h, self.h = self.h, None
