@@ -32,6 +32,11 @@ __device__ __forceinline__ uint32_t rotl32(uint32_t x, int r) {
 __device__ __forceinline__ uint32_t rdl(uint32_t v, uint32_t l) {
     return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l);
 }
+// v[lane l] = x (x and l wave-uniform): v_writelane_b32 (one scalar register per instruction on
+// gfx9, so the lane goes through m0)
+__device__ __forceinline__ void wrl(uint32_t& v, uint32_t x, uint32_t l) {
+    asm("s_mov_b32 m0, %2\n\tv_writelane_b32 %0, %1, m0" : "+v"(v) : "s"(x), "s"(l) : "m0");
+}
 __device__ __forceinline__ int lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0)); }
 
 // Serial scalar walks (one readlane per hop) raise the wave's issue priority so their
@@ -60,6 +65,15 @@ __device__ unsigned long long g_prof[32];
 #else
 #define PROF_NOW() 0ull
 #define PROF_ADD(arr, k, v) ((void)(v))
+#endif
+// Event counts of the match finder for diagnostic builds only (S3HC_DIAG_LEVEL 11): per-wave
+// scalar counters summed into g_enc_cnt, read back with s3hc_diag_enc_counts (tools/enc_counts.py).
+#if defined(S3HC_DIAG_LEVEL) && S3HC_DIAG_LEVEL == 11
+#define S3HC_ENC_COUNT 1
+__device__ unsigned long long g_enc_cnt[16];
+#define CNT_ADD(k, v) ecn[k] += (v)
+#else
+#define CNT_ADD(k, v) ((void)0)
 #endif
 
 // 4 bytes at any LDS byte offset: two aligned dword reads + v_alignbyte.
@@ -1505,14 +1519,16 @@ __device__ __forceinline__ uint32_t hash_pos(uint32_t v, uint32_t b5) {
 }
 
 // The walk's next landing after a match ending at step-relative position np: the first matched
-// lane of the step mask mq probing at or after np, or 64 when there is none in this step
+// lane of the step mask mq probing at or after np, or a value >= 64 when there is none in this
+// step. Branch-free: v_ffbl_b32 answers all ones for 0, so the first set bit of the 64-bit rest
+// is a min of two saturating sums, all ones when the rest is empty. For kk >= 64 the shift
+// wraps, and whatever it finds, kk + tz stays >= 64.
 template <uint32_t kPSt>
 __device__ __forceinline__ uint32_t next_landing(uint64_t mq, uint32_t np) {
     const uint32_t kk = (np + kPSt - 1u) / kPSt;
-    const uint64_t rest = kk < 64u ? mq >> kk : 0ull;
-    const uint32_t lo = (uint32_t)rest, hi = (uint32_t)(rest >> 32);
-    const uint32_t tz = lo ? (uint32_t)__builtin_ctz(lo) : 32u + (uint32_t)__builtin_ctz(hi | 0x80000000u);
-    return rest ? kk + tz : 64u;
+    const uint64_t rest = mq >> (kk & 63u);
+    const uint32_t tz = umin32(ffbl_hw((uint32_t)rest), __builtin_elementwise_add_sat(ffbl_hw((uint32_t)(rest >> 32)), 32u));
+    return __builtin_elementwise_add_sat(kk, tz);
 }
 
 // Stage block bytes [lo, hi) into lds (lds[x - lo]); any alignment. Every lane issues all of
@@ -1628,6 +1644,12 @@ __global__ __launch_bounds__(enc::kGThreads, S3HC_ENC_MINWAVES) S3HC_ENC_WPE_ATT
     uint64_t epr[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     const uint64_t tk0 = PROF_NOW();
 #endif
+#ifdef S3HC_ENC_COUNT
+    // 0 segments, 1 steps with a valid lane, 2 steps that ran the distance-1..4 block, 3..9 those
+    // steps by lanes wanting it (1, 2, 3, 4-7, 8-15, 16-31, 32-64), 10 the sum of those lanes,
+    // 11 walk landings (while (av) iterations), 12 hops, 13 wave-wide extensions
+    uint32_t ecn[14] = {1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#endif
     const uint32_t k = G.y + wv;
     const uint32_t s = B.seg0 + k;
     const uint32_t seg_lo = k * kSeg;
@@ -1643,17 +1665,29 @@ __global__ __launch_bounds__(enc::kGThreads, S3HC_ENC_MINWAVES) S3HC_ENC_WPE_ATT
     int64_t smax = (int64_t)end_lim - 4;
     if ((int64_t)U - 12 < smax) smax = (int64_t)U - 12;
     // prewarm the table with the window before the segment
-    // (four positions per lane from one aligned 8-byte read)
-    {
-        const uint32_t lim = seg_lo - pw_lo;  // window position i is inserted when i + 4 <= lim
-        for (uint32_t d0 = lane; 4 * d0 < lim; d0 += 64) {
-            const uint32_t w0 = dw[d0], w1 = dw[d0 + 1];
+    // (four positions per lane from one aligned 8-byte read). The window is absent (the block's
+    // first segment) or whole: kPrewarm bytes, 256 per iteration, and window position i is
+    // inserted when i + 4 <= kPrewarm, which only the last iteration's last lane can fail (its
+    // positions 1..3 go to the sink). The other iterations have no select and no branch, and an
+    // iteration's read is issued before the hashes of the one before it. The four stores of an
+    // iteration keep their order (j = 0..3, all lanes), so collisions resolve as ever.
+    static_assert(kPrewarm <= kSeg && kPrewarm % 256 == 0, "the prewarm window is whole or absent");
+    if (seg_lo != pw_lo) {
+        auto put = [&](uint32_t w0, uint32_t w1, uint32_t d0, auto last) {
 #pragma unroll
             for (uint32_t j = 0; j < 4; ++j) {
                 const uint32_t i = 4 * d0 + j;
-                tbl[i + 4 <= lim ? hash_pos(__builtin_amdgcn_alignbyte(w1, w0, j), __builtin_amdgcn_ubfe(w1, 8 * j, 8)) : kTbl] = (uint16_t)i;
+                const uint32_t h = hash_pos(j ? __builtin_amdgcn_alignbyte(w1, w0, j) : w0, __builtin_amdgcn_ubfe(w1, 8 * j, 8));
+                tbl[(!decltype(last)::value || j == 0 || i + 4 <= kPrewarm) ? h : kTbl] = (uint16_t)i;
             }
+        };
+        uint32_t d0 = lane, w0 = dw[d0], w1 = dw[d0 + 1];
+        for (uint32_t it = 0; it + 1 < kPrewarm / 256; ++it) {
+            const uint32_t n0 = dw[d0 + 64], n1 = dw[d0 + 65];
+            put(w0, w1, d0, std::false_type{});
+            w0 = n0, w1 = n1, d0 += 64;
         }
+        put(w0, w1, d0, std::true_type{});
     }
     wave_sync();
 #ifdef S3HC_PROF
@@ -1663,9 +1697,13 @@ __global__ __launch_bounds__(enc::kGThreads, S3HC_ENC_MINWAVES) S3HC_ENC_WPE_ATT
     uint32_t last_end = seg_lo;  // end of the last recorded match (literal start)
     uint32_t nseq = 0, body = 0, ll0 = 0;
     uint2* myrec = recs + (size_t)s * kMaxSeqPerSeg;
+    // sb and pw_lo are multiples of 4, so a lane's byte shift and its dword within a step are the
+    // same for every step of the kernel
+    const uint32_t sh = (kPS * (uint32_t)lane) & 3u, la = (kPS * (uint32_t)lane) >> 2;
     const uint32_t pend = smax < (int64_t)seg_lo ? seg_lo : (uint32_t)(smax + 1);  // probe [seg_lo, pend)
     for (uint32_t sb = seg_lo; sb < pend; sb += 64 * kSteps) {
         const uint32_t sb_end = sb + 64 * kSteps < pend ? sb + 64 * kSteps : pend;
+        const uint32_t sa = (sb - pw_lo) >> 2;  // dword of the sub-block's first position
         const uint64_t tc0 = PROF_NOW();
         PROF_ADD(epr, 6, 1);
         // ---- A: table pass
@@ -1674,7 +1712,7 @@ __global__ __launch_bounds__(enc::kGThreads, S3HC_ENC_MINWAVES) S3HC_ENC_WPE_ATT
         for (uint32_t q = 0; q < kPSteps; ++q) {
             const uint32_t P = sb + kStepPos * q + kPS * lane;
             const uint32_t i = P - pw_lo;
-            const uint32_t a = i >> 2, sh = i & 3;
+            const uint32_t a = sa + la + kStepPos / 4 * q;  // i >> 2; sh is i & 3
             const uint32_t w0 = dw[a], w1 = dw[a + 1], wp = dw[(int)a - 1], wpp = dw[(int)a - 2];
             vv[q] = __builtin_amdgcn_alignbyte(w1, w0, sh);
             vm[q] = __builtin_amdgcn_alignbyte(w0, wp, sh);    // bytes [P-4, P)
@@ -1733,7 +1771,7 @@ __global__ __launch_bounds__(enc::kGThreads, S3HC_ENC_MINWAVES) S3HC_ENC_WPE_ATT
             const bool tin = (c16 != kEmpty) & (c16 < i);
             const uint32_t ct = tin ? c16 : i;
 #endif
-            const uint32_t a = i >> 2, sh = i & 3, ta = ct >> 2, ts = ct & 3;
+            const uint32_t a = sa + la + kStepPos / 4 * q, ta = ct >> 2, ts = ct & 3;
             uint32_t O[kNQ + 1], T[kNQ + 3];
 #pragma unroll
             for (int j = 0; j < kNQ + 1; ++j) O[j] = dw[a + 1 + j];
@@ -1769,7 +1807,14 @@ __global__ __launch_bounds__(enc::kGThreads, S3HC_ENC_MINWAVES) S3HC_ENC_WPE_ATT
 #if S3HC_ABL == 2  // diagnostic ablation: no distance-1..4 candidate
             want_short = false;
 #endif
+            CNT_ADD(1, __ballot(valid) ? 1u : 0u);
             if (S3HC_SHORT_CAND == 1 && __ballot(want_short)) {
+#ifdef S3HC_ENC_COUNT
+                const uint32_t wpc = (uint32_t)__builtin_popcountll(__ballot(want_short));
+                CNT_ADD(2, 1);
+                CNT_ADD(3 + (wpc <= 3 ? wpc - 1 : (wpc < 8 ? 3 : (wpc < 16 ? 4 : (wpc < 32 ? 5 : 6)))), 1);
+                CNT_ADD(10, wpc);
+#endif
                 const uint32_t df = (e1 & (i >= 1)) ? 1u : ((e2 & (i >= 2)) ? 2u : ((e3 & (i >= 3)) ? 3u : ((e4 & (i >= 4)) ? 4u : 0u)));
                 gf = want_short & (df != 0);
                 const uint32_t fs = (4u - df) & 3u;
@@ -1831,10 +1876,15 @@ __global__ __launch_bounds__(enc::kGThreads, S3HC_ENC_MINWAVES) S3HC_ENC_WPE_ATT
             // (< 64) when one lies in this step; else 0x100 | the step-relative position after the
             // match (it leaves the step, or no match follows it here); 0x80 for a match that
             // reached kFwd (extended wave-wide first). A hop is one v_readlane, lane to lane.
-            const uint32_t np = kPS * (uint32_t)lane + flen[q];
+            uint32_t fl = flen[q];  // (a register of its own: the walk patches one lane of it in place)
+            uint32_t np = kPS * (uint32_t)lane + fl;
+            asm("" : "+v"(np));  // (range unknown to the optimiser: the landing arithmetic stays 32-bit)
             const uint32_t nl = next_landing<kPS>(mq, np);
-            const uint32_t nxl = flen[q] == kFwd ? 0x80u : (nl < 64u ? nl : 0x100u | np);
-            uint32_t r = x > base ? x - base : 0u;  // < kStepPos
+            const uint32_t nxl = fl == kFwd ? 0x80u : (nl < 64u ? nl : 0x100u | np);
+            // x - base or 0, < kStepPos (signed max: a scalar instruction; an unsigned saturating
+            // subtraction is a vector one plus a v_readfirstlane)
+            const int32_t xr = (int32_t)(x - base);
+            uint32_t r = (uint32_t)(xr > 0 ? xr : 0);
             // the first probed position at or after r (a probe after r reaches back to it)
             uint32_t j0 = (r + kPS - 1u) / kPS;
             uint64_t av = j0 < 64u ? mq & (~0ull << j0) : 0ull;
@@ -1846,7 +1896,9 @@ __global__ __launch_bounds__(enc::kGThreads, S3HC_ENC_MINWAVES) S3HC_ENC_WPE_ATT
             while (av) {
                 uint32_t j = (uint32_t)__builtin_ctzll(av);
                 uint32_t v;
+                CNT_ADD(11, 1);
                 for (;;) {
+                    CNT_ADD(12, 1);
                     hm |= 1ull << j;
                     v = rdl(nxl, j);
                     if (v >= 64u) break;
@@ -1859,6 +1911,7 @@ __global__ __launch_bounds__(enc::kGThreads, S3HC_ENC_MINWAVES) S3HC_ENC_WPE_ATT
                 {  // long match: wave-wide forward extension
                     const uint64_t tx0 = PROF_NOW();
                     PROF_ADD(epr, 8, 1);
+                    CNT_ADD(13, 1);
                     const uint32_t wj = rdl(word[q], j);
                     const uint32_t P = base + kPS * j;
                     const uint32_t maxf = end_lim - P;
@@ -1882,7 +1935,7 @@ __global__ __launch_bounds__(enc::kGThreads, S3HC_ENC_MINWAVES) S3HC_ENC_WPE_ATT
                         lenf += 4u * g + rdl(e2, g);
                         break;
                     }
-                    flen[q] = (uint32_t)lane == j ? lenf : flen[q];
+                    wrl(fl, lenf, j);  // one lane, in place: the loop carries no vector copy
                     r = kPS * j + lenf;
                     PROF_ADD(epr, 2, PROF_NOW() - tx0);
                 }
@@ -1894,7 +1947,7 @@ __global__ __launch_bounds__(enc::kGThreads, S3HC_ENC_MINWAVES) S3HC_ENC_WPE_ATT
                 const uint32_t rank =
                     __builtin_amdgcn_mbcnt_hi((uint32_t)(hm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hm, 0));
                 const uint32_t hidx = (hm >> lane) & 1ull ? nseq - ns_sb + rank : kStash + ((uint32_t)lane & 7u);
-                stash[hidx] = make_uint2((base + kPS * lane - seg_lo) | (flen[q] << 16), word[q]);
+                stash[hidx] = make_uint2((base + kPS * lane - seg_lo) | (fl << 16), word[q]);
                 last_end = base + r;
                 nseq += (uint32_t)__builtin_popcountll(hm);
             }
@@ -1941,6 +1994,10 @@ __global__ __launch_bounds__(enc::kGThreads, S3HC_ENC_MINWAVES) S3HC_ENC_WPE_ATT
     epr[7] = nseq;
     if (lane == 0)
         for (int q = 0; q < 9; ++q) atomicAdd(&g_prof[16 + q], (unsigned long long)epr[q]);
+#endif
+#ifdef S3HC_ENC_COUNT
+    if (lane == 0)
+        for (int q = 0; q < 14; ++q) atomicAdd(&g_enc_cnt[q], (unsigned long long)ecn[q]);
 #endif
     if (lane == 0) {
         SegSummary S;
@@ -2595,6 +2652,19 @@ extern "C" int s3hc_diag_prof(unsigned long long* out, int n, int reset) {
     if (reset) {
         unsigned long long z[32] = {0};
         if (hipMemcpyToSymbol(HIP_SYMBOL(s3hc::g_prof), z, sizeof(z)) != hipSuccess) return -1;
+    }
+    return 0;
+}
+#endif
+
+#ifdef S3HC_ENC_COUNT
+extern "C" int s3hc_diag_enc_counts(unsigned long long* out, int n, int reset) {
+    if (n > 16) n = 16;
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(s3hc::g_enc_cnt), sizeof(unsigned long long) * n) != hipSuccess) return -1;
+    if (reset) {
+        unsigned long long z[16] = {0};
+        if (hipMemcpyToSymbol(HIP_SYMBOL(s3hc::g_enc_cnt), z, sizeof(z)) != hipSuccess) return -1;
     }
     return 0;
 }
